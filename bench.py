@@ -17,22 +17,29 @@ PCIe-inclusive rate).
 stream around the same K steps for the kernel time (= the K launches back to back).  The
 rocprofv3 kernel trace of the same command is summarised by scripts/prof_summary.py.
 
-Beside it (not the headline): the north-star synthetic weight [11008, 4096] (grouped and one
-launch per weight), the AWQ kernels, a 2-layer AWQ oneshot, the other BASELINE configs, and the
-CPU baseline (the oracle's torch restatement on the host cores).
+A plain run does only that: set-up, W warm-up steps, the K timed steps, the result line
+(``ms_per_step`` = wall milliseconds per timed step).  ``--dump-outputs DIR`` also writes what the
+last timed step computed (``dump_outputs``), so two builds can be compared output for output:
+the weights are seeded, the same arguments give the same inputs.
+
+``--full`` adds everything else (not the headline): the steady-state and per-launch figures, the
+multi-GPU legs below, the PCIe-inclusive rate, the north-star synthetic weight [11008, 4096]
+(grouped and one launch per weight), the AWQ kernels, a 2-layer AWQ oneshot, the other BASELINE
+configs, and the CPU baseline (the oracle's torch restatement on the host cores) with the parity
+check of the measured outputs.
 
 Multi-GPU: one process per GPU.  ``--gpus N`` under torchrun (WORLD_SIZE=N) runs as rank
 RANK; ``--gpus N`` without a torchrun environment starts the N ranks itself (a
 ``torch.distributed.run`` child process; this process never touches the GPU), and a mismatch
 between ``--gpus`` and WORLD_SIZE is an error, so ``n_gpus`` is always the ranks that ran
 (``ranks_seen`` = the process group's size).  The headline is weak scaling: each rank
-compresses its own Qwen3-4B-sized weight set (no collective in the timed region).  Beside it,
-at every N: the row-sharded synthetic leg ([11008, 4096] split into N row
+compresses its own Qwen3-4B-sized weight set (no collective in the timed region).  Beside it
+under ``--full``, at every N: the row-sharded synthetic leg ([11008, 4096] split into N row
 blocks, kernel-only and end-to-end including the RCCL all-gather of the packed codes and
 scales) and the strong-scaling leg (ONE Qwen3-4B sharded over the ranks by the product's
 plan, plus ``distributed.gather_state``'s all-gather of the compressed state dict).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N ...
 """
 import argparse
@@ -86,12 +93,17 @@ def parse():
     # 50 untimed steps (70 ms): the clocks settle about 25 steps (35 ms) into a load
     # (scripts/step_ramp.py, profiles/r05j_step_ramp.log), so the K timed steps are steady state
     p.add_argument("--warmup", type=int, default=50)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary leg, the CPU baseline and the parity check (off: headline only)")
     p.add_argument("--copies", type=int, default=12)
     p.add_argument("--cpu-seconds", type=float, default=10.0)
     p.add_argument("--launch-check", action="store_true",
                    help="start the ranks, join the process group, print the rank census and exit (no GPU use)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="headline only (no secondary legs)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU leg")
+    p.add_argument("--no-extras", action="store_true",
+                   help="with --full: only the per-launch, steady-state and multi-GPU legs")
     p.add_argument("--profile-only", action="store_true",
                    help="warmup + K headline steps only (rocprofv3 PMC passes); prints nothing else")
     return p.parse_args()
@@ -725,6 +737,44 @@ def strong_model_leg(units, dev, stream, world, rank, steps=10):
     return res
 
 
+DUMP_BUDGET = 56 << 20  # bytes of array data --dump-outputs may write (the limit is 64 MB in all)
+
+
+def dump_outputs(tensors, out_dir, budget=DUMP_BUDGET):
+    """``--dump-outputs``: write ``tensors`` ({name: tensor}, here ``CompressionPlan.tensors()``
+    after the last timed step: what ``save_compressed`` would put on disk) as
+    ``out_dir/<name>.npy``.  Floating-point tensors are widened to float32 (float64 stays), integer
+    tensors to float64, both exactly.  A tensor no larger than an even share of ``budget`` is written
+    whole in its own shape; the others split what is left evenly, each as a 1-D sample of its
+    flattened elements at sorted indices drawn from a generator seeded with the tensor's rank in the
+    sorted names -- the same arguments give the same indices, so two builds' files compare element
+    for element.  Returns the bytes of array data written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(tensors.items())
+
+    def wide(t):
+        return torch.float32 if t.dtype.is_floating_point and t.dtype != torch.float64 else torch.float64
+
+    def nbytes(t):
+        return t.numel() * (4 if wide(t) == torch.float32 else 8)
+
+    share = budget // max(len(items), 1)
+    n_big = sum(1 for _, t in items if nbytes(t) > share)
+    share = (budget - sum(nbytes(t) for _, t in items if nbytes(t) <= share)) // max(n_big, 1)
+    written = 0
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        if nbytes(t) > share:
+            n = share // (nbytes(t) // t.numel())
+            idx = torch.randint(0, t.numel(), (n,), generator=torch.Generator().manual_seed(i)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        arr = t.to(wide(t)).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        written += arr.nbytes
+    return written
+
+
 def _spawn_ranks(n: int) -> int:
     """``--gpus N`` outside a torchrun environment: run N rank processes of this script under
     ``torch.distributed.run`` as a CHILD process (this process never initialises the GPU and
@@ -753,89 +803,16 @@ def launch_check(world, rank, backend):
     dist.destroy_process_group()
 
 
-def main():
-    args = parse()
-    env_world = os.environ.get("WORLD_SIZE")
-    if env_world is None and (args.gpus or 1) > 1:
-        sys.exit(_spawn_ranks(args.gpus))  # the ranks print the line; nothing here touches the GPU
-    world = int(env_world or "1")
-    if args.gpus is not None and args.gpus != world:
-        print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: refusing to report an n_gpus the run "
-              f"does not have", file=sys.stderr)
-        sys.exit(2)
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    # QZ_BENCH_BACKEND=gloo: rehearsal of the multi-rank code path on a box with fewer GPUs than
-    # ranks (ranks share devices, collectives go through host memory); the driver's N-GPU runs
-    # use the default RCCL ("nccl") backend, one rank per GPU.
-    backend = os.environ.get("QZ_BENCH_BACKEND", "nccl")
-    if args.launch_check:
-        launch_check(world, rank, backend)
-        return
-    n_dev = torch.cuda.device_count()  # counts devices without initialising the GPU
-    if backend == "gloo":
-        local = local % max(n_dev, 1)
-    elif world > 1 and n_dev < world:
-        print(f"bench.py: {world} ranks need {world} GPUs for RCCL, {n_dev} visible "
-              f"(QZ_BENCH_BACKEND=gloo rehearses the ranks on fewer)", file=sys.stderr)
-        sys.exit(2)
-    if world > 1:
-        torch.cuda.set_device(local)
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-        else:
-            dist.init_process_group(backend)
-    dev = torch.device("cuda", local)
-    torch.cuda.set_device(dev)
-
+def full_legs(args, held, dev, stream, world, rank, backend, stamp):
+    """``--full``: everything beside the headline, after its timed region, on the same model, units
+    and plan (``held`` = [model, units, plan], emptied here so that they are freed before the legs
+    that build their own weights).  Returns the fields the legs add to the result line."""
     from quantizers_amd import ops
-    from quantizers_amd.compressor import CompressionPlan, compression_units
     from quantizers_amd.quantization import QuantizationArgs
-
-    phases = {}  # per-rank wall seconds by phase (max over ranks goes in the line)
-    t_phase = [T_START]
-
-    def stamp(name):
-        now = time.perf_counter()
-        phases[name] = phases.get(name, 0.0) + now - t_phase[0]
-        t_phase[0] = now
-
-    stamp("start_to_device")
-    torch.manual_seed(1234 + rank)
-    model = build_model(dev)
-    units, _ = compression_units(model)
-    plan = CompressionPlan(units, dev)  # every pointer table / output built before timing
-    stream = torch.cuda.current_stream(dev)
+    model, units, plan = held
+    del held[:]
     params_step = plan.params
     alg_step = plan.alg_bytes()
-    launches_step = plan.launches
-
-    def region(k):
-        """barrier + sync, exactly k steps, sync + barrier: (wall s max over ranks, event ms)."""
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        e0.record(stream)
-        for _ in range(k):
-            plan.run(stream)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        wall = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
-        if world > 1:
-            _all_reduce_max(wall)
-        return wall.item(), e0.elapsed_time(e1)
-
-    stamp("model_and_plan")
-    for _ in range(args.warmup):
-        plan.run(stream)
-    el, ev_ms = region(args.steps)
-    stamp("headline")
-    if args.profile_only:
-        return
 
     # steady state of the same plan (informational, never `value`): 100 steps after 50 more; equal
     # to the timed region at the default W = 50 (the clocks settle about 25 steps into a load,
@@ -876,7 +853,6 @@ def main():
 
     # multi-GPU legs (BASELINE.md §2 multi-GPU row; north star: RCCL all-gather over xGMI), run at
     # every N so the driver's 1/2/4/8-GPU lines carry comparable fields
-    ranks_seen = dist.get_world_size() if world > 1 else 1
     stamp("per_launch_and_checks")
     strong = strong_model_leg(units, dev, stream, world, rank, steps=10 if backend == "nccl" else 2)
     stamp("strong_scaling_leg")
@@ -930,6 +906,102 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu, ok = cpu_baseline(args.cpu_seconds, checks + ([cpu_check] if cpu_check else []))
     stamp("cpu_baseline")
+    more = {"per_launch": per_launch, "steady_state": steady, "cpu_baseline": cpu, "parity_check": ok,
+            "row_sharded_synthetic_11008x4096": row_sharded, "strong_scaling_qwen3_4b_sharded": strong,
+            "pcie_inclusive": pcie}
+    more.update(extras)
+    return more
+
+
+def main():
+    args = parse()
+    env_world = os.environ.get("WORLD_SIZE")
+    if env_world is None and (args.gpus or 1) > 1:
+        sys.exit(_spawn_ranks(args.gpus))  # the ranks print the line; nothing here touches the GPU
+    world = int(env_world or "1")
+    if args.gpus is not None and args.gpus != world:
+        print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: refusing to report an n_gpus the run "
+              f"does not have", file=sys.stderr)
+        sys.exit(2)
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    # QZ_BENCH_BACKEND=gloo: rehearsal of the multi-rank code path on a box with fewer GPUs than
+    # ranks (ranks share devices, collectives go through host memory); the driver's N-GPU runs
+    # use the default RCCL ("nccl") backend, one rank per GPU.
+    backend = os.environ.get("QZ_BENCH_BACKEND", "nccl")
+    if args.launch_check:
+        launch_check(world, rank, backend)
+        return
+    n_dev = torch.cuda.device_count()  # counts devices without initialising the GPU
+    if backend == "gloo":
+        local = local % max(n_dev, 1)
+    elif world > 1 and n_dev < world:
+        print(f"bench.py: {world} ranks need {world} GPUs for RCCL, {n_dev} visible "
+              f"(QZ_BENCH_BACKEND=gloo rehearses the ranks on fewer)", file=sys.stderr)
+        sys.exit(2)
+    if world > 1:
+        torch.cuda.set_device(local)
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+        else:
+            dist.init_process_group(backend)
+    dev = torch.device("cuda", local)
+    torch.cuda.set_device(dev)
+
+    from quantizers_amd.compressor import CompressionPlan, compression_units
+
+    phases = {}  # per-rank wall seconds by phase (max over ranks goes in the line)
+    t_phase = [T_START]
+
+    def stamp(name):
+        now = time.perf_counter()
+        phases[name] = phases.get(name, 0.0) + now - t_phase[0]
+        t_phase[0] = now
+
+    stamp("start_to_device")
+    torch.manual_seed(1234 + rank)
+    model = build_model(dev)
+    units, _ = compression_units(model)
+    plan = CompressionPlan(units, dev)  # every pointer table / output built before timing
+    stream = torch.cuda.current_stream(dev)
+    params_step = plan.params
+    alg_step = plan.alg_bytes()
+    launches_step = plan.launches
+
+    def region(k):
+        """barrier + sync, exactly k steps, sync + barrier: (wall s max over ranks, event ms)."""
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record(stream)
+        for _ in range(k):
+            plan.run(stream)
+        e1.record(stream)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        wall = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
+        if world > 1:
+            _all_reduce_max(wall)
+        return wall.item(), e0.elapsed_time(e1)
+
+    stamp("model_and_plan")
+    for _ in range(args.warmup):
+        plan.run(stream)
+    el, ev_ms = region(args.steps)
+    stamp("headline")
+    if args.profile_only:
+        return
+    if args.dump_outputs:
+        if rank == 0:
+            dump_outputs(plan.tensors(), args.dump_outputs)
+        stamp("dump_outputs")  # on every rank: the phase names are all-reduced below, so all ranks hold the same
+    ranks_seen = dist.get_world_size() if world > 1 else 1
+    held = [model, units, plan]  # the only references left: full_legs empties it to free them before its later legs
+    del model, units, plan
+    more = full_legs(args, held, dev, stream, world, rank, backend, stamp) if args.full else {}
     names = sorted(phases)
     pt = torch.tensor([phases[k] for k in names], device=dev, dtype=torch.float64)
     if world > 1:
@@ -988,18 +1060,12 @@ def main():
                                           "(K x launches_per_step grouped launches back to back) / launches",
                          "event_ms_per_step": ev_ms / args.steps,
                          "traffic_unit": "HBM bytes per launch (alg_bytes_per_launch beside it)"},
-            "per_launch": per_launch,
-            "steady_state": steady,
-            "cpu_baseline": cpu,
-            "parity_check": ok,
             "ranks_seen": ranks_seen,
-            "row_sharded_synthetic_11008x4096": row_sharded,
-            "strong_scaling_qwen3_4b_sharded": strong,
-            "pcie_inclusive": pcie,
+            "full": args.full,
             "phase_seconds_max_rank": phase_max,
             "wall_seconds_max_rank": round(sum(phase_max.values()), 3),
         }
-        line.update(extras)
+        line.update(more)  # --full: the secondary legs, the CPU baseline and the parity check
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

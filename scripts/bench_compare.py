@@ -1,5 +1,6 @@
 """Leg-by-leg comparison of two bench.py lines (the JSON line of each log): every numeric timing
-field (ms / us / value / frac), the relative difference, and the largest difference.
+field (ms / us / value / frac), the relative difference, and the largest difference.  The legs
+beside the headline are in the line only when bench.py ran with --full.
 usage: python scripts/bench_compare.py a.log b.log"""
 import json
 import sys

@@ -34,5 +34,5 @@ timeout -k 2 10 rocm-smi --showpower --showclocks --showtemp > $OUT/smi_idle.txt
 run first_touch 120 python3 scripts/first_touch.py
 run idle_gap 120 python3 scripts/idle_gap.py
 QZ_BENCH_BACKEND=gloo run bench_gloo_n2 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2
+    --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --full
 echo "=== done"

@@ -7,6 +7,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 TAG=${TAG:-r05}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the whole line: every secondary leg, CPU baseline, parity check
 export TMPDIR=/tmp
 if [ -n "${TUNE:-}" ]; then
   timeout -k 10 420 python -u scripts/tune_block.py $TUNE > gpurun_out/${TAG}_tune_block.log 2>&1 || exit $?

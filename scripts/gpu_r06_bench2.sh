@@ -4,6 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"; mkdir -p gpurun_out; export TMPDIR=/tmp
 TAG=${TAG:-r06e}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # every leg is compared, so every leg is run
 for i in 1 2; do
   timeout -k 10 300 python bench.py ${BENCH_ARGS:-} > gpurun_out/${TAG}_bench$i.log 2>&1 || { tail -20 gpurun_out/${TAG}_bench$i.log; exit 1; }
   echo "bench $i done"

@@ -7,6 +7,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 TAG=${TAG:-r03}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the whole line: every secondary leg, CPU baseline, parity check
 export TMPDIR=/tmp
 step() {  # step <name> <timeout> <cmd...>
   local name=$1 to=$2; shift 2

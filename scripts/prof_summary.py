@@ -5,8 +5,8 @@ and cross-check the bench line's roofline against the profiler's kernel duration
   python scripts/prof_summary.py TAG PROF_DIR BENCH_LOG
 
 PROF_DIR holds rocprofv3's ``*_kernel_trace.csv`` / ``*_kernel_stats.csv`` of
-``rocprofv3 --kernel-trace --stats -- python3 bench.py --steps K --warmup W``; BENCH_LOG is that
-command's stdout (its JSON line).  Writes
+``rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps K --warmup W``; BENCH_LOG is
+that command's stdout (its JSON line, with the ``per_launch`` leg that only ``--full`` runs).  Writes
   profiles/TAG_kernel_stats.csv   -- the stats table (torch generator names shortened)
   profiles/TAG_bench_line.json    -- the bench line of the same run
   profiles/TAG_headline.json      -- the headline launches picked from the trace: the grouped

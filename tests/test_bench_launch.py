@@ -43,6 +43,38 @@ def test_gpus_mismatch_with_world_size_fails():
     assert not [x for x in r.stdout.splitlines() if x.startswith("{")]
 
 
+def test_dump_outputs_is_exact_bounded_and_repeatable(tmp_path):
+    """``--dump-outputs``: small tensors whole and exact in float32 / float64, large ones as the
+    same seeded sample on every call, the whole dump within the byte budget."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(3)
+    packed = torch.randint(-2 ** 31, 2 ** 31 - 1, (300, 40), generator=g, dtype=torch.int64).to(torch.int32)
+    tensors = {"m.weight_packed": packed,
+               "m.weight_scale": torch.rand(300, 7, generator=g).to(torch.bfloat16),
+               "m.weight_shape": torch.tensor([300, 320]),
+               "n.weight_packed": packed[:2]}
+    budget = 40_000  # m.weight_packed (96 kB as float64) must be sampled, the others fit
+    wrote = bench.dump_outputs(tensors, str(tmp_path / "a"), budget=budget)
+    assert bench.dump_outputs(tensors, str(tmp_path / "b"), budget=budget) == wrote <= budget
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in tensors}
+    assert sum(a.nbytes for a in got.values()) == wrote
+    for n in tensors:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / (n + ".npy"))), n
+    assert got["m.weight_scale"].dtype == np.float32 and got["m.weight_scale"].shape == (300, 7)
+    assert np.array_equal(got["m.weight_scale"], tensors["m.weight_scale"].float().numpy())
+    assert got["m.weight_shape"].dtype == np.float64 and got["m.weight_shape"].tolist() == [300, 320]
+    assert np.array_equal(got["n.weight_packed"], packed[:2].double().numpy())
+    s = got["m.weight_packed"]
+    assert s.dtype == np.float64 and s.ndim == 1 and 1000 < s.size < packed.numel()
+    assert np.isin(s, packed.double().numpy()).all()
+    other = dict(tensors, **{"m.weight_packed": packed.flip(0).contiguous()})
+    bench.dump_outputs(other, str(tmp_path / "c"), budget=budget)  # same indices, other values
+    assert not np.array_equal(s, np.load(tmp_path / "c" / "m.weight_packed.npy"))
+    assert bench.DUMP_BUDGET <= 60_000_000
+
+
 @pytest.mark.parametrize("world", [1, 2, 3, 4, 5, 7, 8, 16])
 def test_row_blocks_cover_the_weight(world):
     import bench

@@ -1,5 +1,6 @@
-"""Recipe parsing (CPU): the reference's recipe files (when /root/reference is mounted) and this
-repo's configs parse into the expected modifiers / schemes; target matching semantics."""
+"""Recipe parsing (CPU): the reference's recipe, run-config and calibration-set files (settings
+only, stored under tests/golden/reference_configs/) and this repo's configs parse into the
+expected modifiers / schemes; target matching semantics."""
 import glob
 import os
 
@@ -9,7 +10,7 @@ from quantizers_amd.quantization import QuantizationArgs, preset_scheme
 from quantizers_amd.recipe import AWQModifier, QuantizationModifier, is_match, parse_recipe
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/configs/recipes"
+REF = os.path.join(ROOT, "tests", "golden", "reference_configs", "recipes")
 
 
 def test_repo_recipes_parse():
@@ -34,7 +35,6 @@ def test_mixed_recipe_two_modifiers():
     assert len(mods[1].mappings) == 2
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference not mounted")
 @pytest.mark.parametrize("name", ["recipe_awq_w4a16.yaml", "recipe_mixed_fp8_int4.yaml",
                                   "recipe_Minimax-M2.1-AWQ-MixedPrec.yaml", "recipe_Minimax-M2.1-Experts-only-AWQ.yaml",
                                   "recipe_MoE_RTN_NVFP4.yaml", "recipe_Dense_NVFP4.yaml"])
@@ -55,7 +55,6 @@ def test_reference_recipes(name):
         assert len(m.mappings) == 4
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference not mounted")
 def test_autoround_is_out_of_scope():
     with pytest.raises(NotImplementedError):
         parse_recipe(os.path.join(REF, "recipe_AR_W4A16G32.yaml"))
@@ -125,7 +124,6 @@ def test_run_config(tmp_path):
         load_run_config(str(bad)).resolve_recipe()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference not mounted")
 def test_reference_run_configs_resolve():
     """Every run config the reference ships (configs/*.yaml) loads with the reference's path rules:
     recipe found and parsed, calibration-set file found and validated, output dir named as
